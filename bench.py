@@ -12,9 +12,16 @@ parameter.  Inputs are resident in HBM before the timed region.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-One JSON line on rank 0 (contract in the task statement) carrying `roofline` and
-`cpu_baseline` objects.  N > 1: scenes shard data-parallel (8 per rank, weak
-scaling); gradients are summed with ONE RCCL all-reduce of a flat fp32 buffer.
+One JSON line on rank 0: `metric`, `value` (scenes/s), `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` (milliseconds of one timed step) and the configuration.  A
+plain run sets up, warms up, times --steps steps and prints that line; `--full`
+adds everything measured beside it (per-kernel timings in eager runs after the
+timed region, the `roofline` objects and their own runs, the un-pipelined
+`in_step` structure, the `cpu_baseline` leg).  `--dump-outputs DIR` runs one
+more step of the timed path from the initial state and writes what it computed
+to DIR/<name>.npy.  N > 1: scenes shard
+data-parallel (8 per rank, weak scaling); gradients are summed with ONE RCCL
+all-reduce of a flat fp32 buffer.
 """
 import os
 
@@ -317,18 +324,60 @@ def run_cpu_baseline(args):
                 "sample": f"cpu leg exceeded {args.cpu_timeout} s and was stopped"}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: name -> tensor of the dumped step, written as out_dir/<name>.npy in float32 (float64 for float64
+    and integer tensors).  Arrays above the per-array cap -- the largest power of two that keeps the whole dump within
+    DUMP_BYTES -- are written as a fixed sample of their flattened values: positions drawn by a generator seeded with the
+    name, so every run with the same arguments writes the same positions.  Returns name -> (shape written, sampled)."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+
+    def out_dtype(t):
+        return torch.float32 if t.dtype.is_floating_point and t.dtype != torch.float64 or t.dtype == torch.bool else torch.float64
+    items = sorted(arrays.items())
+    cap = 1 << 40
+    while cap > 1 and sum(min(t.numel(), cap) * out_dtype(t).itemsize for _, t in items) > DUMP_BYTES:
+        cap //= 2
+    written = {}
+    for name, t in items:
+        t = t.detach()
+        sampled = t.numel() > cap
+        if sampled:
+            pos = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        a = t.to(out_dtype(t)).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = (list(a.shape), sampled)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event timings (--kernel-steps eager "
+                         "runs after the timed region), the roofline objects and their own runs, the un-pipelined structure "
+                         "(--in-step-steps) and the host-CPU baseline.  Off (default): set up, warm up, time --steps steps, "
+                         "print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps run one more step of the timed path (the same graphs, the next batch) "
+                         "from the initial state -- seeded weights and buffers, zero optimizer state -- and write what it "
+                         "computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all): its loss, the forward's "
+                         "end_points and the updated parameters and gradients of the flat buffers (arrays above their share "
+                         "of the budget as a fixed, seeded sample).  The same arguments give the same outputs to fp32 "
+                         "rounding in every run")
     ap.add_argument("--per-gpu", type=int, default=8, help="scenes per GPU")
     ap.add_argument("--points", type=int, default=50000)
     ap.add_argument("--queries", type=int, default=256)
     ap.add_argument("--tokens", type=int, default=80)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-scenes", type=int, default=4)
-    ap.add_argument("--cpu-threads", type=int, default=64, help="cap on host threads of the CPU leg")
+    ap.add_argument("--cpu-threads", type=int, default=64, help="cap on host threads of the CPU leg (--full)")
     ap.add_argument("--cpu-baseline-only", action="store_true",
                     help="internal: run only the host-CPU leg and print its JSON object")
     ap.add_argument("--cpu-timeout", type=int, default=150)
@@ -371,7 +420,7 @@ def main():
                          "the static buffers while step i runs; here the copy is device-to-device): the pipelined step is "
                          "measured with a CHANGING batch.  1 = the same batch every step")
     ap.add_argument("--in-step-steps", type=int, default=8,
-                    help="N = 1, default launch structure: additionally time this many steps of the un-pipelined structure "
+                    help="--full, N = 1, default launch structure: additionally time this many steps of the un-pipelined structure "
                          "(one graph, sampling and text encoder inside the step: --text-stream 0 --fps-prefetch 0) and "
                          "report them under `in_step` of the same line; 0 = skip")
     ap.add_argument("--attn-dtype", choices=["f32", "bf16", "f16"], default="f32",
@@ -400,7 +449,7 @@ def main():
     ap.add_argument("--split-graphs", action="store_true",
                     help="use the N>1 graph structure (two graphs, eager all-reduce slot) even at N=1")
     ap.add_argument("--kernel-steps", type=int, default=3,
-                    help="eager steps (after the timed region) used for the per-kernel event timings in graph mode")
+                    help="--full: eager steps (after the timed region) used for the per-kernel event timings in graph mode")
     ap.add_argument("--text-encoder-mode", choices=["train", "eval"], default="train",
                     help="train (default, the reference: main_utils.py:459 puts the WHOLE model in train mode, so the frozen RoBERTa "
                          "runs with its dropout layers active) or eval (no dropout inside the frozen encoder: what rounds 1-5 timed)")
@@ -420,8 +469,9 @@ def main():
         s_ = socket.socket(); s_.bind(("127.0.0.1", 0)); port = s_.getsockname()[1]; s_.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        print("[bench] --gpus %d without WORLD_SIZE: re-launching as %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
-        os.execv(sys.executable, cmd)
+        print("[bench] --gpus %d without WORLD_SIZE: launching %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -556,6 +606,18 @@ def main():
         def loss_fn(end_points, batch):
             return synthetic_loss(end_points)
 
+    step_end_points = {}
+    if args.dump_outputs:
+        # keep the forward's end_points alive: under a captured step they are the graph's static outputs, rewritten by every
+        # replay, so after the timed region they hold what its last step computed (held here, their memory is not reused
+        # later in the step)
+        loss_of_end_points = loss_fn
+
+        def loss_fn(end_points, batch):
+            step_end_points.clear()
+            step_end_points.update((k, v) for k, v in end_points.items() if torch.is_tensor(v))
+            return loss_of_end_points(end_points, batch)
+
     ingraph_hist = None
     if os.environ.get("EDA_BENCH_INGRAPH_HIST") == "1":
         ingraph_hist = (torch.full((4096,), 0.0, device=device), torch.full((1,), 0, dtype=torch.long, device=device))
@@ -666,6 +728,11 @@ def main():
     def log(msg):
         if rank == 0:
             print(f"[bench +{time.perf_counter() - t_start:7.1f}s] {msg}", file=sys.stderr, flush=True)
+
+    init_state = None
+    if args.dump_outputs:
+        # the state every run starts from (seeded initialisation), for the dumped step below
+        init_state = (flat.flat_param.clone(), [b_.clone() for b_ in model.buffers()])
 
     log("model + inputs ready")
     eager_step = step
@@ -786,7 +853,30 @@ def main():
         with torch.no_grad():
             log("loss of the last timed step %.3f; eager forward with the trained parameters: %.3f"
                 % (final_loss, float(loss_fn(model(inputs), inputs))))
-    if args.graph:
+    if args.dump_outputs:
+        # The dumped step: one more step of the timed path (the same graphs, the next batch of the same sequence), run from
+        # the state every run starts from -- the seeded initial weights and buffers, zero optimizer moments and step
+        # counters.  The trained weights of the timed steps are not such an input: in the default mode the fp32-atomic
+        # gradient sums differ in their last bits from run to run, and W + N AdamW steps grow that into different
+        # weights; one step from a fixed state reproduces to rounding.
+        barrier()
+        with torch.no_grad():
+            flat.flat_param.copy_(init_state[0])
+            for b_, b0_ in zip(model.buffers(), init_state[1]):
+                b_.copy_(b0_)
+            for st_ in opt.state.values():
+                for v_ in st_.values():
+                    if torch.is_tensor(v_):
+                        v_.zero_()
+        barrier()
+        loss_d = step()
+        barrier()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, dict(step_end_points, loss=loss_d.detach().double().reshape(1),
+                                                          flat_params=flat.flat_param, flat_grads=flat.flat_grad))
+            log("outputs of one step from the initial state -> %s: %d arrays, sampled: %s" % (
+                args.dump_outputs, len(dumped), ", ".join(k for k, (_, s_) in dumped.items() if s_) or "none"))
+    if args.graph and args.full:
         # graph replay runs no host code, so per-kernel HIP events cannot be interleaved with
         # it: time the native kernels in a few eager runs of the SAME step right after.
         for _ in range(2):
@@ -801,7 +891,8 @@ def main():
     # trained inside it (the reference's loop structure) -- timed in the same run so that both schedules are on the
     # driver's clock
     in_step = None
-    if args.graph and not dist_on and args.text_stream and not args.overlap and not args.split_graphs and args.in_step_steps > 0:
+    if args.full and args.graph and not dist_on and args.text_stream and not args.overlap and not args.split_graphs \
+            and args.in_step_steps > 0:
         try:
             g_one = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
@@ -844,9 +935,9 @@ def main():
         from eda_amd import sync_bn as _sbn
         _sbn.check()
     log(f"timed region done: {dt / args.steps * 1e3:.1f} ms/step")
-    if rank == 0:
-        ms_per_step = dt / args.steps * 1e3
-        scenes = args.per_gpu * world * args.steps
+    ms_per_step = dt / args.steps * 1e3
+    scenes = args.per_gpu * world * args.steps
+    if rank == 0 and args.full:
         # launches tagged "side" (eda_amd.ext.tagged: the frozen text encoder) run on the second stream under the pipelined
         # schedule, i.e. off the critical path
         pipelined_sched = bool(args.graph and args.text_stream and not args.overlap)
@@ -1139,6 +1230,7 @@ def main():
         fps = [k for k in kernels if k["op"] == "furthest_point_sampling"]
         fps_info = [{"n": k["dims"][1], "m": k["dims"][2], "ms": k["ms"],
                      "us_per_round": round(k["ms"] * 1e3 / max(1, k["dims"][2] - 1), 3)} for k in fps]
+    if rank == 0:
         out = {
             "metric": "scenes/sec fwd+bwd (50k pts, 256 queries, 80 tok)",
             "value": round(scenes / dt, 3), "unit": "scenes/s", "n_gpus": world,
@@ -1190,38 +1282,41 @@ def main():
                        "roberta_gemm_selection": ("TunableOp (%s; shipped results %s)" % (
                            args.gemm_tuning, "loaded" if shipped_ok else "not used"))
                        if args.gemm_tuning != "off" else "library default"},
-            "roofline": roofline,
-            "launch_bound_gemm": launch_bound_gemm,
-            "roofline_hbm": roofline_hbm,
-            "roofline_hbm_eval": roofline_hbm_eval,
-            "roofline_mfma": roofline_mfma,
-            "roofline_gemm": roofline_gemm,
-            "in_step": in_step,
-            "native_ms_per_step": round(native_ms, 3),
-            "step_matrix": {"gflop_per_step": round((mat["main"] + mat["side"]) / 1e9, 1), "gflop_main_stream": round(mat["main"] / 1e9, 1),
-                            "gflop_second_stream": round(mat["side"] / 1e9, 1),
-                            "tflops_over_the_step": round((mat["main"] + mat["side"]) / (ms_per_step * 1e-3) / 1e12, 2),
-                            "frac_of_nominal_fp32_mfma": round((mat["main"] + mat["side"]) / (ms_per_step * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
-                            "frac_of_measured_issue_rate": round((mat["main"] + mat["side"]) / (ms_per_step * 1e-3) / 1e12 / MFMA_F32_MEASURED_TFLOPS, 4),
-                            "note": "algorithmic FLOPs of every product-shaped native call of one step (attention, row products, SA "
-                                    "stacks, weight gradients, the frozen text encoder) over the step's wall time: the share of the fp32 "
-                                    "matrix pipe the WHOLE step keeps busy (its bf16 x 3 kernels are counted at their fp32 FLOPs)"},
-            "fps": fps_info,
-            "kernel_timing": (("HIP events on the launch stream, %d eager runs of the same step after the "
-                               "graph-replayed timed region" % args.kernel_steps) if args.graph else
-                              "HIP events on the launch stream inside the timed region") +
-                             "; per op and shape the median bracket (mean below five calls)",
-            "kernels": kernels[:40],
-            "gemm_family_ms_per_step": round(sum(k["ms"] * k["calls_per_step"] for k in kernels
-                                                 if k["op"].startswith(("gemm_", "sa_fused", "wgrad"))), 3),
             "source_hash": source_hash(),
             "loss": final_loss,
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = run_cpu_baseline(args)
-        if os.environ.get("EDA_BENCH_KERNELS_FILE"):       # the complete per-op table (the line carries the first 40 rows)
-            with open(os.environ["EDA_BENCH_KERNELS_FILE"], "w") as f:
-                json.dump(kernels, f)
+        if args.full:
+            out.update({
+                "roofline": roofline,
+                "launch_bound_gemm": launch_bound_gemm,
+                "roofline_hbm": roofline_hbm,
+                "roofline_hbm_eval": roofline_hbm_eval,
+                "roofline_mfma": roofline_mfma,
+                "roofline_gemm": roofline_gemm,
+                "in_step": in_step,
+                "native_ms_per_step": round(native_ms, 3),
+                "step_matrix": {"gflop_per_step": round((mat["main"] + mat["side"]) / 1e9, 1), "gflop_main_stream": round(mat["main"] / 1e9, 1),
+                                "gflop_second_stream": round(mat["side"] / 1e9, 1),
+                                "tflops_over_the_step": round((mat["main"] + mat["side"]) / (ms_per_step * 1e-3) / 1e12, 2),
+                                "frac_of_nominal_fp32_mfma": round((mat["main"] + mat["side"]) / (ms_per_step * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
+                                "frac_of_measured_issue_rate": round((mat["main"] + mat["side"]) / (ms_per_step * 1e-3) / 1e12 / MFMA_F32_MEASURED_TFLOPS, 4),
+                                "note": "algorithmic FLOPs of every product-shaped native call of one step (attention, row products, SA "
+                                        "stacks, weight gradients, the frozen text encoder) over the step's wall time: the share of the fp32 "
+                                        "matrix pipe the WHOLE step keeps busy (its bf16 x 3 kernels are counted at their fp32 FLOPs)"},
+                "fps": fps_info,
+                "kernel_timing": (("HIP events on the launch stream, %d eager runs of the same step after the "
+                                   "graph-replayed timed region" % args.kernel_steps) if args.graph else
+                                  "HIP events on the launch stream inside the timed region") +
+                                 "; per op and shape the median bracket (mean below five calls)",
+                "kernels": kernels[:40],
+                "gemm_family_ms_per_step": round(sum(k["ms"] * k["calls_per_step"] for k in kernels
+                                                     if k["op"].startswith(("gemm_", "sa_fused", "wgrad"))), 3),
+            })
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = run_cpu_baseline(args)
+            if os.environ.get("EDA_BENCH_KERNELS_FILE"):       # the complete per-op table (the line carries the first 40 rows)
+                with open(os.environ["EDA_BENCH_KERNELS_FILE"], "w") as f:
+                    json.dump(kernels, f)
         # the JSON line is the LAST line of stdout: RCCL prints a version banner through C stdio (buffered until exit when
         # stdout is a pipe) -- flush it out first
         try:

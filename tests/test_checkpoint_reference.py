@@ -1,6 +1,8 @@
-"""Checkpoint interchange with the REFERENCE (main_utils.py:126-166, :279-301), exercised with the
-reference's own model and optimizer classes imported in the build container (tools/ref_import.py) -- skipped where
-/root/reference does not exist (the GPU box):
+"""Checkpoint interchange with the REFERENCE (main_utils.py:126-166, :279-301).  The reference model is
+stood in for by a module with exactly its state_dict layout -- names, shapes, dtypes, parameter or buffer, requires_grad,
+in the reference's order (tests/golden/checkpoint_layout.json, written from the reference's own classes by
+tools/gen_golden_checkpoint_layout.py) -- filled with the same deterministic values, so the reference's optimizer groups
+and per-parameter AdamW state come out as the reference's would:
   * a checkpoint written in the reference's layout from the reference model (DistributedDataParallel `module.` prefix,
     config namespace, per-parameter AdamW state of the three learning-rate groups) loads strictly into
     eda_amd.BeaUTyDETR and -- through FlatParams' layout -- into the flat optimizer: the next update step equals the
@@ -8,16 +10,45 @@ reference's own model and optimizer classes imported in the build container (too
   * a checkpoint written by eda_amd.checkpoint.save_checkpoint loads into the reference model and optimizer (strict)
     and continues identically."""
 import argparse
+import json
 import os
-import sys
 
-import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="needs the reference checkout (build container only)")
+LAYOUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "checkpoint_layout.json")
 
 LRS = {"base": 1e-4, "backbone_net": 1e-3, "text_encoder": 1e-5}           # scripts/train_scanrefer.sh
+
+
+def _reference_model():
+    """The reference model's state_dict layout as a module tree; its text encoder is model_fixtures.small_roberta(1),
+    frozen (bdetr.py:78-80), in the place the reference registers it."""
+    import model_fixtures as MF
+    records = json.load(open(LAYOUT))
+    root = torch.nn.Module()
+    for name, shape, dtype, kind, requires_grad in records:
+        if name.startswith("text_encoder."):
+            if "text_encoder" not in root._modules:
+                root.text_encoder = MF.small_roberta(1)
+                for p in root.text_encoder.parameters():
+                    p.requires_grad = False
+            continue
+        *path, leaf = name.split(".")
+        m = root
+        for part in path:
+            if part not in m._modules:
+                m.add_module(part, torch.nn.Module())
+            m = m._modules[part]
+        t = torch.zeros(shape, dtype=getattr(torch, dtype))
+        if kind == "param":
+            m.register_parameter(leaf, torch.nn.Parameter(t, requires_grad=requires_grad))
+        else:
+            m.register_buffer(leaf, t)
+    params = dict(root.named_parameters())
+    got = [[k, list(v.shape), str(v.dtype).replace("torch.", ""), "param" if k in params else "buffer",
+            params[k].requires_grad if k in params else False] for k, v in root.state_dict().items()]
+    assert got == records, "stand-in layout differs from the reference's"
+    return root
 
 
 def _ref_optimizer(model):
@@ -49,17 +80,11 @@ def _step_flat(model, flat, opt, seed):
 
 
 def test_reference_checkpoint_interchange(tmp_path):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import ref_import
     import model_fixtures as MF
     from eda_amd import checkpoint
     from eda_amd.bdetr import BeaUTyDETR
     from eda_amd.parallel import FlatParams, reference_lr_groups
-    mods = ref_import.load()
-    ref = ref_import.build_reference_model(mods, seed=0, num_queries=64, butd=True)
-    ref.text_encoder = MF.small_roberta(1)
-    for p in ref.text_encoder.parameters():
-        p.requires_grad = False                                             # bdetr.py:78-80
+    ref = _reference_model()
     MF.fill_det_state(ref, seed=30)
     ref_opt = _ref_optimizer(ref)
     assert len(ref_opt.param_groups) == 3 and len(ref_opt.param_groups[2]["params"]) == 0
@@ -94,16 +119,13 @@ def test_reference_checkpoint_interchange(tmp_path):
                 for n, p in mine.named_parameters() if p.requires_grad)
     assert worst < 1e-6, worst
 
-    # ---- and back: written here, loaded by the reference's classes (strict, as main_utils.py:135 does)
+    # ---- and back: written here, loaded into the reference's layout (strict, as main_utils.py:135 does)
     path2 = str(tmp_path / "ckpt_epoch_8.pth")
     checkpoint.save_checkpoint(mine, path2, optimizer=opt, epoch=8, flat=flat,
                                config=argparse.Namespace(lr=1e-4))
     ck = torch.load(path2, map_location="cpu", weights_only=False)
     assert set(ck) >= {"config", "save_path", "model", "optimizer", "scheduler", "epoch"} and ck["epoch"] == 8
-    ref2 = ref_import.build_reference_model(mods, seed=1, num_queries=64, butd=True)
-    ref2.text_encoder = MF.small_roberta(1)
-    for p in ref2.text_encoder.parameters():
-        p.requires_grad = False
+    ref2 = _reference_model()
     hf = ("text_encoder.embeddings.position_ids", "text_encoder.embeddings.token_type_ids")
     sd = {k[len("module."):]: v for k, v in ck["model"].items()}
     res = ref2.load_state_dict(sd, strict=False)

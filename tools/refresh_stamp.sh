@@ -5,7 +5,7 @@ tag=${1:-refresh}; O=gpurun_out/$tag; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1; tail -1 $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
 python tools/measure_traffic.py > $O/traffic.txt 2>&1
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tools/prof_gemm_shapes.sh ${tag} > /dev/null 2>&1
 python - "$O" <<'PY'
 import json, sys
