@@ -156,6 +156,9 @@ SIGNATURES = {
                                  _p, _p, _i, _i, _p, _p, _p, _sz, _p, _p, _p, _p, _l, _p, _p]),
     "eda_sa_fused_bwd_wt_f32": (_i, [_p, _p, _p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _l, _i, _p, _p, _p,
                                     _p, _p, _p, _i, _i, _p, _p, _p, _sz, _p, _p, _p, _p, _l, _p, _p]),
+    "eda_det_decode_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "eda_det_nms_f64": (_i, [_p, _p, _p, _i, _i, ctypes.c_double, _i, _i, _p, _p]),
+    "eda_det_match_f64": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

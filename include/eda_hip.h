@@ -811,6 +811,33 @@ int eda_peer_allreduce_f64(double *buf, long n, void *stream);
 int eda_peer_bn_hook(void *user, double *buf, long n, void *stream);
 int eda_set_bn_sync_native(int world);
 
+/* ScanNet detection mAP (csrc/det_eval.hip; eda_amd/ap_helper.py is the drop-in for the reference's models/ap_helper.py).
+ * All box and IoU arithmetic is fp64 in the reference's operation order; boxes are camera-frame AABBs
+ * (x1, y1, z1, x2, y2, z2).  The IoU is axis-aligned: for the heading-0 boxes EDA predicts it is the quantity the
+ * reference's box3d_iou (utils/box_util.py:100-122, polygon clipping + ConvexHull) computes, up to rounding.
+ *   eda_det_decode_f32  center, pred_size (n, 3), sem_cls_scores (n, C1), optional objectness logits (n) ->
+ *                       aabb (n, 6) fp64 [flip_axis_to_camera + get_3d_box, heading 0: size halves in fp32],
+ *                       obj_prob (n), cls_prob (n, C1 - 1) [softmax; with logits: sigmoid objectness; without:
+ *                       obj = 1 - p[C], p[:C] / obj -- models/ap_helper.py:142-156], sem_cls (n) = first arg-max of
+ *                       the raw logits over the first C1 - 1 columns.  n = B * K.
+ *   eda_det_nms_f64     greedy 3D NMS per scene (utils/nms.py nms_3d_faster / _samecls): descending score, ties to the
+ *                       larger index; o = inter / ((area_i + area_j) - inter) (old_type: inter / area_j), times the
+ *                       class-equality gate when cls_nms; a box is suppressed when o > iou_thresh.  K <= 1024.
+ *                       keep (B, K) = 1 for picked boxes.  cls may be NULL when cls_nms == 0.
+ *   eda_det_match_f64   AP matching (utils/eval_det.py:211-237), one wave per (threshold, class, scene): predictions of
+ *                       (scene s, class c) are the j with pred_valid[s][j] and (pred_cls == NULL or pred_cls[s][j] == c),
+ *                       confidence conf[s][j][conf_cols == 1 ? 0 : c], taken in descending confidence (ties: ascending
+ *                       j, NaN last); each is a TP when the first-maximum IoU against the scene's ground truth of class
+ *                       c (gt_cls[s][g] == c; -1 = no box) exceeds thresholds[t] and that box is not matched yet.
+ *                       tp (T, C, S, K) = 1 for true positives, 0 elsewhere.  K <= 1024, G <= 1024. */
+int eda_det_decode_f32(const float *center, const float *pred_size, const float *sem_cls_scores, const float *obj_logits,
+                       int B, int K, int C1, double *aabb, float *obj_prob, float *cls_prob, int *sem_cls, void *stream);
+int eda_det_nms_f64(const double *aabb, const double *score, const int *cls, int B, int K, double iou_thresh,
+                    int old_type, int cls_nms, unsigned char *keep, void *stream);
+int eda_det_match_f64(const double *pred_aabb, const double *conf, int conf_cols, const int *pred_cls,
+                      const unsigned char *pred_valid, const double *gt_aabb, const int *gt_cls, const double *thresholds,
+                      int S, int K, int G, int C, int T, unsigned char *tp, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
