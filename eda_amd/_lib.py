@@ -159,6 +159,9 @@ SIGNATURES = {
     "eda_det_decode_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "eda_det_nms_f64": (_i, [_p, _p, _p, _i, _i, ctypes.c_double, _i, _i, _p, _p]),
     "eda_det_match_f64": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "eda_augment_layout": (_i, [_p]),
+    "eda_augment_batch_f64": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l,
+                                   ctypes.c_ulonglong, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

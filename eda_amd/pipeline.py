@@ -112,7 +112,7 @@ def _side_stream(device):
 class PipelinedTrainStep:
     def __init__(self, model, first_batch, loss_fn, backward_fn, update_fn, *, stream=None, all_reduce=None,
                  split_update=False, prefetch="sa1", text_prefetch=True, after_loss=None, sa1_samples=2048,
-                 post_stages=None):
+                 post_stages=None, pre_stage=None):
         """model: BeaUTyDETR (train mode, text encoder frozen).  first_batch: dict of DEVICE tensors (the layout of
         every later batch; extra tensors, e.g. loss targets, ride along).  loss_fn(end_points, batch) -> scalar.  backward_fn(loss): backward + gradient gather (e.g. under
         FlatParams.deferred_wgrad()).  update_fn(): clip + optimizer step (capturable).  all_reduce(): eager
@@ -124,7 +124,12 @@ class PipelinedTrainStep:
         prefetch: "sa1" (SA1's sampling for the next batch), "geometry" (everything the backbone derives from the
         coordinates alone: Pointnet2Backbone.geometry) or None (sampling inside the step; then the text encoder runs for
         the CURRENT batch underneath the point backbone).  text_prefetch: the text encoder, too, works for the next batch.
-        stream: the stream the graphs are captured / replayed on (warm-up eager steps must have run on it)."""
+        stream: the stream the graphs are captured / replayed on (warm-up eager steps must have run on it).
+        pre_stage: a capturable stage with `produces` / `consumes` (batch keys) and `bind(inputs, outputs)`, e.g.
+        augment.AugmentStage: it is captured as its own small graph on the side stream and replayed after a batch is fed
+        and before the prefetch, reading the fed batch's `consumes` keys and writing its `produces` keys (which
+        `next_batch` may then omit; the batch is copied by key).  first_batch holds every key; the first batch trained is
+        the stage's result on first_batch's inputs."""
         prefetch_geometry = prefetch == "geometry"
         text_prefetch = bool(text_prefetch) and prefetch is not None
         self.model, self.loss_fn = model, loss_fn
@@ -164,6 +169,14 @@ class PipelinedTrainStep:
         self.nxt, self.cur = _rebuild(first_batch, self._nxt_flat), _rebuild(first_batch, self._cur_flat)
         self.inds_next, self.inds_cur = nv[nb:nb + ni], cv[nb:nb + ni]
         self.text_prefetch = text_prefetch
+        self.pre_stage, self.g_pre = pre_stage, None
+        if pre_stage is not None:
+            # the stage reads the fed batch's inputs and writes the keys it produces, all in the nxt buffers
+            pre_stage.bind(inputs={k: self.nxt[k] for k in pre_stage.consumes},
+                           outputs={k: self.nxt[k] for k in pre_stage.produces})
+            self.g_pre = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_pre, stream=self.side, **mode):
+                pre_stage()
         # the text encoder reads the NEXT batch's tokens when it is prefetched, else the current batch's
         tok = (self.nxt if text_prefetch else self.cur)["tokenized"]
 
@@ -194,6 +207,8 @@ class PipelinedTrainStep:
             else:
                 self.text_next = hidden
         self.side.synchronize()
+        if self.g_pre is not None:
+            self.g_pre.replay()
         if self.g_fps is not None:
             self.g_fps.replay()
         self.g_text.replay()
@@ -242,12 +257,30 @@ class PipelinedTrainStep:
 
     def _feed(self, batch):
         """Copy `batch` (same layout as the first one) into the nxt buffers, on the side stream."""
+        if self.pre_stage is not None:
+            return self._feed_by_key(batch)
         src = _flat(batch)
         for v, t in zip(self._nxt_flat, src):
             v.copy_(t)
         for t in src:                       # the copy runs on the side stream: keep the caller's memory alive until it is done
             if t.is_cuda:                   # (host / pinned sources have no stream bookkeeping: record_stream raises)
                 t.record_stream(self.side)
+
+    def _feed_by_key(self, batch):
+        """With a pre_stage: copy every key of the layout except those the stage produces (which `batch` may omit)."""
+        skip = set(self.pre_stage.produces)
+        for k, dst in self.nxt.items():
+            if k in skip and k not in batch:
+                continue
+            if k not in batch:
+                raise KeyError(f"next_batch lacks {k!r}")
+            pairs = [(dst[kk], batch[k][kk]) for kk in dst] if isinstance(dst, dict) else [(dst, batch[k])]
+            for v, t in pairs:
+                if not torch.is_tensor(v):
+                    continue
+                v.copy_(t)
+                if t.is_cuda:
+                    t.record_stream(self.side)
 
     def step(self, next_batch=None):
         """Train on the batch fed by the previous call (the first batch initially); start the sampling / text encoding
@@ -275,6 +308,8 @@ class PipelinedTrainStep:
                 self.ev_text.record(self.side)
             if next_batch is not None:
                 self._feed(next_batch)
+            if self.g_pre is not None:
+                self.g_pre.replay()            # (the stage runs every step, as the loader's host work did)
             if self.g_fps is not None and "fps" not in _TIMING_SKIP:
                 self.g_fps.replay()
             if self.text_prefetch and "text" not in _TIMING_SKIP:

@@ -838,6 +838,36 @@ int eda_det_match_f64(const double *pred_aabb, const double *conf, int conf_cols
                       const unsigned char *pred_valid, const double *gt_aabb, const int *gt_cls, const double *thresholds,
                       int S, int K, int G, int C, int T, unsigned char *tp, void *stream);
 
+/* Train-time scene augmentation and box targets (csrc/augment.hip; eda_amd/augment.py: SceneBank, draw_params,
+ * augment_batch, AugmentStage).  Replaces the point-dependent part of the reference's Joint3DDataset.__getitem__:
+ * _augment (src/joint_det_dataset.py:421-466), the box targets of _get_target_boxes (:684-715) and _get_scene_objects
+ * (:717-754) with Scan._set_axis_align_bbox (src/visual_data_handlers.py:246-260), and the box transform and augment_det
+ * of _get_detected_objects (:785-855).  Two launches per batch, capturable: no host sync, no allocation.
+ *   eda_augment_layout     out[6] = {int row stride, fp64 row stride, 132 rows, 1024 objects per scan, offset of the
+ *                          target ids in the int row, offset of the target jitters in the fp64 row}
+ *   eda_augment_batch_f64  bank: xyz (n_slots, n_points, 3) fp64, color (.., 3) fp32, obj (n_slots, n_points) int16
+ *                          (-1 = no object, else < n_obj), det_box (n_slots, 132, 6) fp64 centre / size, det_cls
+ *                          (n_slots, 132) int32.  Per scene b: ints[b] (slot, n targets, target ids, keep mask, class
+ *                          ids for det_mode 2), params[b] (rotation matrices, flips, shift, scale, box-level draws).
+ *                          Points: flips, rot_z, rot_x, rot_y, + noise, + shift, * scale in fp64, one rounding;
+ *                          colour ((c - mean) + mean) * f - mean.  augment == 0: identity, colour c - mean, no jitter.
+ *                          noise / color_factor (B, n_points, 3) fp64 are the explicit draws; NULL: Philox4x32-10 keyed
+ *                          by seed, counter (point, b << 2 | call, *counter or counter_value); *counter is then
+ *                          incremented by the second launch.  ws: B * n_obj * 6 uint64, initially
+ *                          (~0, ~0, ~0, 0, 0, 0) per object, and left so.  Outputs: point_clouds (B, n_points, 3 + 3 *
+ *                          use_color) fp32, og_color (B, n_points, 3), point_instance_label (B, n_points) int64,
+ *                          center_label / size_gts (B, 132, 3), box_label_mask (B, 132), all_bboxes (B, 132, 6),
+ *                          det_boxes (B, 132, 6) fp32, det_class_ids (B, 132) int64.  det_mode: 0 zeros, 1 the
+ *                          detector's boxes (+ augment_det), 2 a copy of all_bboxes (butd_gt / butd_cls). */
+int eda_augment_layout(int *out);
+int eda_augment_batch_f64(const double *xyz, const float *color, const short *obj, const double *det_box,
+                          const int *det_cls, long n_slots, int n_points, int n_obj, const int *ints, const double *params,
+                          int B, int augment, int use_color, int det_mode, int augment_det, const double *noise,
+                          const double *color_factor, long *counter, long counter_value, unsigned long long seed,
+                          unsigned long long *ws, float *point_clouds, float *og_color, long *point_instance_label,
+                          float *center_label, float *size_gts, float *box_label_mask, float *all_bboxes,
+                          float *det_boxes, long *det_class_ids, void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
