@@ -162,6 +162,11 @@ SIGNATURES = {
     "eda_augment_layout": (_i, [_p]),
     "eda_augment_batch_f64": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l,
                                    ctypes.c_ulonglong, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "eda_ground_decode_lds_bytes": (_sz, [_i, _i, _i]),
+    "eda_ground_decode_supported": (_i, [_i, _i, _i]),
+    "eda_ground_decode_f32": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p,
+                                   _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p,
+                                   _p]),
 }
 
 _lib = None

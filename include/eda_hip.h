@@ -868,6 +868,37 @@ int eda_augment_batch_f64(const double *xyz, const float *color, const short *ob
                           float *center_label, float *size_gts, float *box_label_mask, float *all_bboxes,
                           float *det_boxes, long *det_class_ids, void *stream);
 
+/* Language grounding from the model's outputs to ranked boxes and accuracy counters in ONE launch
+ * (csrc/ground_decode.hip; eda_amd/inference.py: decode_grounding, DeviceGroundingEvaluator).  Replaces, for P prediction
+ * heads at once, the reference's GroundingEvaluator.evaluate_bbox_by_pos_align (src/grounding_evaluator.py:139-224) and
+ * evaluate_bbox_by_sem_align (:226-372) with their per-sample host loops, _parse_gt (:374-394) and the `last_`
+ * break-downs (:330-372): 14 chains of ~20 launches and 14 device-to-host copies per batch at 7 heads.
+ *   score of query q for object o = sum_t p[q,t] * ([positive_map[b,o,t] > 0] + (modify + pron + rel - other)[b,0,t]),
+ *   p = softmax over the Ts token scores (position alignment) or over the L logits proj_queries . proj_tokens / 0.07
+ *   (semantic alignment), zero beyond them up to the map width T; with det_boxes the score is multiplied by
+ *   [max IoU with a masked detected box > 0.25].  Per (head, alignment, scene, object) the K <= 16 queries of highest
+ *   score, lowest query first among equals: top_query (-1 where Q < K), top_score, top_box (centre, size),
+ *   top_corners (min, max; sizes clamped at 1e-6), top_iou with the object's ground-truth box -- all
+ *   (P, A, B, G, K[, 6]) with A = number of alignments in align_mask (1 position, 2 semantic, 3 both, position first).
+ *   Objects are the first G of the Gs rows of the maps / ground truth (G = 1: root only).
+ *   counters (int64, ADDED to with vector atomics, never zeroed here): [P][2 alignments][nthr * ntopk found-at-(t, k) of
+ *   the objects o < min(sum box_label_mask[b], G), then that number of objects], followed by the break-downs of head
+ *   last_prefix (-1: none) under the semantic alignment at top-1 of object 0: [threshold 0, 1][view-dep, hard, unique]
+ *   [flag on, off][found, count].  Any of the auxiliary maps / ground truth / gate / outputs / counters may be NULL as a
+ *   group.  Dot products, softmax sums and score sums are fp64.  Capturable: no workspace, no host synchronisation. */
+size_t eda_ground_decode_lds_bytes(int Q, int T, int G);
+int eda_ground_decode_supported(int Q, int T, int G);
+int eda_ground_decode_f32(int P, const float *const *sem_cls_scores, const float *const *proj_queries,
+                          const float *const *center, const float *const *pred_size, const float *proj_tokens,
+                          const float *positive_map, const float *modify_map, const float *pron_map, const float *rel_map,
+                          const float *other_map, const float *gt_center, long gt_center_stride, const float *gt_size,
+                          const float *box_label_mask, const float *det_boxes, const unsigned char *det_mask,
+                          const unsigned char *is_view_dep, const unsigned char *is_hard, const unsigned char *is_unique,
+                          int B, int Q, int Ts, int L, int D, int T, int Gs, int G, int Dn, int align_mask, int K, int nthr,
+                          const float *thresholds, int ntopk, const int *topks, int last_prefix, int *top_query,
+                          float *top_score, float *top_box, float *top_corners, float *top_iou, long *counters,
+                          void *stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
