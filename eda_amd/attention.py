@@ -13,6 +13,10 @@ backward is one more kernel (dQ, dK, dV in one pass) that recomputes them.
 
 ``attention_core`` has no CPU path (the HIP library is the product); the torch
 restatement used by CPU-side tests lives in oracle/attention_ref.py.
+
+Attention maps: ``attention_core_weights``, ``MultiheadAttention.forward(need_weights=True)`` and the
+``record_weights`` context manager return the probabilities (head mean or per head) from one extra launch
+(csrc/mha_weights.hip) that reads q, k, the mask and the forward's lse; nothing changes when nobody asks.
 """
 import itertools
 import os
@@ -179,6 +183,55 @@ def _mha_fwd_call(q, k, v, m8, B, num_heads, Lq, Lk, hd, p_drop, salt, out, lse)
     _lib.check(rc, "eda_mha_fwd_ws")
 
 
+# ---- attention maps (csrc/mha_weights.hip) --------------------------------------------------------------------------
+# The forward leaves lse, so the probabilities are one more launch from the q, k and mask the autograd node holds.  A
+# request is posted here by the caller (attention_core_weights, MultiheadAttention.forward) around the node's forward;
+# without one (every training / inference path) the nodes do exactly what they did before.
+_weights_request = None      # None, or per_head (bool)
+_weights_result = None
+
+
+def _mha_weights_call(q, k, m8, lse, num_heads, p_drop, salt, per_head):
+    """exp(scale q.k - lse) per head [x the forward's dropout keep mask / (1 - p)], head mean unless per_head: one launch
+    of eda_mha_weights_f32 (include/eda_hip.h).  fp32 whatever compute dtype the forward ran in."""
+    q, k = _rows(q), _rows(k)
+    B, Lq, D = q.shape
+    Lk = k.shape[1]
+    hd = D // num_heads
+    dev = q.device
+    w = torch.empty((B, num_heads, Lq, Lk) if per_head else (B, Lq, Lk), dtype=torch.float32, device=dev)
+    seed = dropout_state(dev) if p_drop > 0 else None
+    with torch.cuda.device(dev), _timed('mha_weights', (B, num_heads, Lq, Lk)):
+        rc = _lib.lib().eda_mha_weights_f32(
+            q.data_ptr(), k.data_ptr(), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+            m8.data_ptr() if m8 is not None else None, lse.data_ptr(), B, num_heads, Lq, Lk, hd, hd ** -0.5,
+            float(p_drop), seed.data_ptr() if seed is not None else None, int(salt), int(bool(per_head)),
+            w.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "eda_mha_weights_f32")
+    return w
+
+
+def _post_weights(q, k, m8, lse, num_heads, p_drop, salt):
+    global _weights_result
+    if _weights_request is not None:
+        _weights_result = _mha_weights_call(q.detach(), k.detach(), m8, lse, num_heads, p_drop, salt, _weights_request)
+
+
+def _torch_weights(q, k, key_padding_mask, num_heads, per_head):
+    """The torch form of the map (CPU path; what the GPU tests compare the launch against): fp32 logits per head, -inf on
+    masked keys, softmax, head mean.  No dropout."""
+    B, Lq, D = q.shape
+    Lk = k.shape[1]
+    hd = D // num_heads
+    qh = q.detach().float().view(B, Lq, num_heads, hd).transpose(1, 2)
+    kh = k.detach().float().view(B, Lk, num_heads, hd).transpose(1, 2)
+    s = (qh * hd ** -0.5) @ kh.transpose(-1, -2)
+    if key_padding_mask is not None:
+        s = s.masked_fill(key_padding_mask.bool()[:, None, None, :], float("-inf"))
+    w = torch.softmax(s, dim=-1)
+    return w if per_head else w.mean(1)
+
+
 class _FusedMHA(Function):
     @staticmethod
     def forward(ctx, q, k, v, mask, num_heads, p_drop, salt):
@@ -194,6 +247,7 @@ class _FusedMHA(Function):
         if mask is not None:
             m8 = mask.contiguous().view(torch.uint8)
         _mha_fwd_call(q, k, v, m8, B, num_heads, Lq, Lk, hd, p_drop, salt, out, lse)
+        _post_weights(q, k, m8, lse, num_heads, p_drop, salt)
         ctx.dtype_code = _compute_dtype
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.mask8 = m8
@@ -322,6 +376,7 @@ class _ProjectedMHA(Function):
             out = torch.empty((B, Lq, d), dtype=torch.float32, device=dev)
             lse = torch.empty((B, num_heads, Lq), dtype=torch.float32, device=dev)
             _mha_fwd_call(q, k, v, m8, B, num_heads, Lq, Lk, hd, p_drop, salt, out, lse)
+        _post_weights(q, k, m8, lse, num_heads, p_drop, salt)
         ctx.dtype_code = _compute_dtype
         ctx.save_for_backward(W, out, lse, b, *x2s, *Ps)
         ctx.mask8 = m8
@@ -492,6 +547,7 @@ class _ProjectedMHAPreKV(Function):
             out = torch.empty((B, Lq, d), dtype=torch.float32, device=dev)
             lse = torch.empty((B, num_heads, Lq), dtype=torch.float32, device=dev)
             _mha_fwd_call(q, k, v, m8, B, num_heads, Lq, Lk, hd, p_drop, salt, out, lse)
+        _post_weights(q, k, m8, lse, num_heads, p_drop, salt)
         ctx.dtype_code = _compute_dtype
         ctx.save_for_backward(W, b, x2, q, kv, out, lse)
         ctx.mask8 = m8
@@ -547,6 +603,80 @@ def attention_core(q, k, v, key_padding_mask=None, num_heads=8, dropout_p=0.0, s
     return _core(q, k, v, key_padding_mask, num_heads, dropout_p, salt)
 
 
+def attention_core_weights(q, k, v, key_padding_mask=None, num_heads=8, dropout_p=0.0, salt=0, per_head=False):
+    """attention_core that also returns the attention probabilities: (out, weights) with weights (B,Lq,Lk) -- the mean
+    over the heads, torch.nn.MultiheadAttention's average_attn_weights=True -- or (B,H,Lq,Lk) with per_head.  CUDA
+    tensors: the fused forward, then ONE launch (csrc/mha_weights.hip) that rebuilds every probability from the
+    forward's lse and, with dropout_p > 0, the forward's own keep mask and 1/(1-p) (so weights @ v IS out); fp32 for
+    every set_compute_dtype.  CPU tensors: the torch form (fp32 softmax with masked fill, head mean; dropout_p > 0 draws
+    from torch's generator).  `weights` is DETACHED: gradients flow through `out` only.  Masked keys are exactly 0; a row
+    whose keys are all masked is NaN."""
+    global _weights_request, _weights_result
+    if q.is_cuda:
+        _weights_request, _weights_result = bool(per_head), None
+        try:
+            out = _FusedMHA.apply(q, k, v, key_padding_mask, num_heads, dropout_p, salt)
+            w = _weights_result
+        finally:
+            _weights_request = _weights_result = None
+        return out, w
+    B, Lk, D = v.shape
+    hd = D // num_heads
+    qh = q.float().view(B, -1, num_heads, hd).transpose(1, 2)
+    kh = k.float().view(B, Lk, num_heads, hd).transpose(1, 2)
+    vh = v.float().view(B, Lk, num_heads, hd).transpose(1, 2)
+    sc = (qh * hd ** -0.5) @ kh.transpose(-1, -2)
+    if key_padding_mask is not None:
+        sc = sc.masked_fill(key_padding_mask.bool()[:, None, None, :], float("-inf"))
+    p = torch.softmax(sc, dim=-1)
+    if dropout_p > 0:
+        p = F.dropout(p, dropout_p)
+    out = (p @ vh).transpose(1, 2).reshape(B, -1, D)
+    w = p.detach()
+    return out, (w if per_head else w.mean(1))
+
+
+_recording = None            # record_weights: {id(module): [(key, per_head, dict), ...]}
+
+
+class record_weights:
+    """Context manager: `with record_weights(model, sites, per_head=False) as maps:` -- inside, the named attention modules
+    leave their map of every forward in maps[site] ((B,Lq,Lk), or (B,H,Lq,Lk) with per_head; detached; the last call
+    wins).  The model reaches its attention modules through fused residual blocks (skip_out_proj / pre_kv), so their
+    return value is out of reach; here the modules launch the weights kernel from the q, k, mask and lse their autograd
+    node already holds -- outputs are bit-identical to an unrecorded forward.  `sites`: names of MultiheadAttention
+    instances as model.named_modules() gives them ("decoder.5.cross_l"), or a suffix of one that is unique
+    ("5.cross_l"); the dict is keyed by the string passed.  Unknown or ambiguous: KeyError listing the choices.  Eager
+    execution only: a recorded forward under stream capture raises RuntimeError.  Contexts nest: a module named by several open contexts serves each of them from one
+    launch.  Outside the context nothing changes."""
+
+    def __init__(self, model, sites, per_head=False):
+        if isinstance(sites, str):
+            sites = [sites]
+        mods = {n: m for n, m in model.named_modules() if isinstance(m, MultiheadAttention)}
+        self.maps, self.entries = {}, {}
+        for s_ in sites:
+            hit = [n for n in mods if n == s_] or [n for n in mods if n.endswith("." + s_)]
+            if len(hit) != 1:
+                raise KeyError("record_weights: %s attention site %r; choices: %s"
+                               % ("ambiguous" if hit else "unknown", s_, ", ".join(sorted(hit or mods))))
+            self.entries.setdefault(id(mods[hit[0]]), []).append((s_, bool(per_head), self.maps))
+        self.prev = None
+
+    def __enter__(self):
+        global _recording
+        self.prev = _recording
+        _recording = {k: list(v) for k, v in (self.prev or {}).items()}       # nested contexts: every recorder is served
+        for k, e in self.entries.items():
+            _recording.setdefault(k, []).extend(e)
+        return self.maps
+
+    def __exit__(self, *exc):
+        global _recording
+        _recording = self.prev
+        return False
+
+
 class _OutProj(nn.Linear):
     pass
 
@@ -579,14 +709,45 @@ class MultiheadAttention(nn.Module):
 
     def forward(self, query, key, value, key_padding_mask=None, need_weights=False,
                 attn_mask=None, batch_first=False, defer_out_bias=False, skip_out_proj=False, pre_kv=None,
-                residual=None):
-        """Returns (output, None).  Inputs are (L,B,F) unless batch_first (then (B,L,F)).
+                residual=None, average_attn_weights=True):
+        """Returns (output, None), or (output, weights) with need_weights=True: the attention probabilities as
+        torch.nn.MultiheadAttention returns them, (B,Lq,Lk) averaged over the heads, or (B,H,Lq,Lk) with
+        average_attn_weights=False -- batch first whatever batch_first says, detached (gradients flow through output
+        only), in training mode the dropped and rescaled probabilities the output was built from (HIP path; the CPU
+        path returns them without dropout).  On the HIP path they cost one extra launch (csrc/mha_weights.hip).
+        Inputs are (L,B,F) unless batch_first (then (B,L,F)).
         With defer_out_bias the out-projection is applied WITHOUT its bias and (output, bias) is
-        returned: the caller's fused residual+LayerNorm kernel adds it (fused_ln.py).
+        returned: the caller's fused residual+LayerNorm kernel adds it (fused_ln.py); with need_weights=True the
+        second value is the weights and the caller takes the bias from out_proj.bias.
         With skip_out_proj (HIP path only, see hip_path) the attention output BEFORE the out-projection is
         returned: the caller's fused kernel applies out_proj together with the residual LayerNorm."""
         if attn_mask is not None:
             raise NotImplementedError("EDA always passes attn_mask=None")
+        rec = _recording.get(id(self)) if _recording is not None else None
+        if not need_weights and rec is None:
+            return self._forward(query, key, value, key_padding_mask, batch_first, defer_out_bias, skip_out_proj,
+                                 pre_kv, residual)
+        global _weights_request, _weights_result
+        if rec is not None and query.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("eda_amd.attention.record_weights: attention maps are recorded in eager execution only, "
+                               "not while the stream is being captured into a HIP graph")
+        per_head = (need_weights and not average_attn_weights) or (rec is not None and any(r[1] for r in rec))
+        _weights_request, _weights_result = per_head, None
+        try:
+            o, second = self._forward(query, key, value, key_padding_mask, batch_first, defer_out_bias, skip_out_proj,
+                                      pre_kv, residual)
+            w = _weights_result
+        finally:
+            _weights_request = _weights_result = None
+        for key_, ph_, maps_ in rec or ():
+            maps_[key_] = w if (ph_ or not per_head) else w.mean(1)
+        if need_weights:
+            return o, (w if (not average_attn_weights or not per_head) else w.mean(1))
+        return o, second
+
+    def _forward(self, query, key, value, key_padding_mask, batch_first, defer_out_bias, skip_out_proj, pre_kv,
+                 residual):
+        global _weights_result
         if pre_kv is not None:
             # K | V of this module were projected together with its siblings' (_StackedKV): q-projection + core only
             assert batch_first and skip_out_proj and self.hip_path(query)
@@ -641,6 +802,8 @@ class MultiheadAttention(nn.Module):
             q = F.linear(query, W[:d], b[:d])
             k = F.linear(key, W[d:2 * d], b[d:2 * d])
             v = F.linear(value, W[2 * d:], b[2 * d:])
+        if _weights_request is not None:
+            _weights_result = _torch_weights(q, k, key_padding_mask, self.num_heads, _weights_request)
         o = attention_core(q, k, v, key_padding_mask, self.num_heads,
                            self.dropout if self.training else 0.0, self._salt)
         o = F.linear(o, self.out_proj.weight, None if defer_out_bias else self.out_proj.bias)

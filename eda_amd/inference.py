@@ -615,7 +615,7 @@ class GroundingSession:
         return SceneHandle(pc, ep)
 
     def ground(self, point_cloud, utterances=None, detected_boxes=None, topk=10, *, tokenized=None, positive_map=None,
-               alignment="semantic", prefix="last_", scene=None):
+               alignment="semantic", prefix="last_", scene=None, explain=False):
         """point_cloud: (N, 3 + C) device tensor (ignored when `scene`, the handle a previous call returned, is given).
         utterances: list of U strings (needs a tokenizer) or a dict {"input_ids", "attention_mask"} of (U, L) tensors;
         `tokenized=` is the same dict by keyword.  detected_boxes: None or (boxes (D, 6), mask (D,), class_ids (D,)) for a
@@ -624,7 +624,13 @@ class GroundingSession:
         NON-SPECIAL tokens of each sentence (attention_mask without the first <s> and the last </s> token), every word
         counting alike.  alignment: "semantic" (the reference's `bbf`, the one its `last_` break-downs are taken on) or
         "position".  Returns a dict: boxes (U, topk, 6) centre + size, corners (U, topk, 6), scores (U, topk),
-        queries (U, topk), scene (the handle) and end_points."""
+        queries (U, topk), scene (the handle) and end_points.
+        explain=True adds "explain": why these boxes -- head-averaged attention maps (eda_amd.attention.record_weights: one
+        extra launch per recorded module, every other output bit-identical), with S seed points and L tokens:
+        token_to_seeds (U, L, S) the last encoder layer's text <- points map (cross_lv), query_to_tokens (U, topk, L) and
+        query_to_seeds (U, topk, S) the rows of the last decoder layer's cross_l / cross_v maps for the returned
+        `queries`, seed_xyz (S, 3) and seed_inds (S,) (indices into the point cloud).  upsample_to_points() spreads an
+        (..., S) map over the N input points."""
         model = self.model
         if isinstance(utterances, dict) and tokenized is None:
             tokenized, utterances = utterances, None
@@ -652,8 +658,16 @@ class GroundingSession:
             inputs["det_class_ids"] = cls.to(dev)[None].expand(U, -1).contiguous()
         ep = {k: (v.expand(U, *v.shape[1:]).contiguous() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == 1 else v)
               for k, v in scene.end_points.items()}
+        maps = None
         with torch.no_grad():
-            ep = model.forward_rest(inputs, ep)
+            if explain:
+                from .attention import record_weights
+                sites = (f"cross_encoder.layers.{len(model.cross_encoder.layers) - 1}.cross_layer.cross_lv",
+                         f"decoder.{model.num_decoder_layers - 1}.cross_l", f"decoder.{model.num_decoder_layers - 1}.cross_v")
+                with record_weights(model, sites) as maps:
+                    ep = model.forward_rest(inputs, ep)
+            else:
+                ep = model.forward_rest(inputs, ep)
             if positive_map is None:
                 T = 256
                 n_tok = am.sum(1, keepdim=True)
@@ -665,6 +679,34 @@ class GroundingSession:
                 positive_map = positive_map[:, None, :]
             out = decode_grounding(ep, prefixes=(prefix,), topk=topk, targets={"positive_map": positive_map.to(dev).float()},
                                    only_root=True, alignment=alignment)
-        return {"boxes": out["top_box"][0, 0, :, 0], "corners": out["top_corners"][0, 0, :, 0],
-                "scores": out["top_score"][0, 0, :, 0], "queries": out["top_query"][0, 0, :, 0], "scene": scene,
-                "end_points": ep}
+        res = {"boxes": out["top_box"][0, 0, :, 0], "corners": out["top_corners"][0, 0, :, 0],
+               "scores": out["top_score"][0, 0, :, 0], "queries": out["top_query"][0, 0, :, 0], "scene": scene,
+               "end_points": ep}
+        if explain:
+            lv, cl, cv = (maps[s_] for s_ in sites)
+            rows = res["queries"].long()[:, :, None]
+            res["explain"] = {"token_to_seeds": lv,
+                              "query_to_tokens": torch.gather(cl, 1, rows.expand(-1, -1, cl.shape[2])),
+                              "query_to_seeds": torch.gather(cv, 1, rows.expand(-1, -1, cv.shape[2])),
+                              "seed_xyz": scene.end_points["fp2_xyz"][0], "seed_inds": scene.end_points["fp2_inds"][0]}
+        return res
+
+
+def upsample_to_points(seed_map, scene):
+    """(..., S) values on the seed points of `scene` (a SceneHandle; e.g. a row of explain["query_to_seeds"]) -> (..., N)
+    on its input points, for colouring the cloud: the backbone's own feature propagation rule (PointnetFPModule,
+    pointnet2/pointnet2_modules.py: three nearest seeds, weights 1 / (distance + 1e-8) normalised) on the existing
+    three_nn / three_interpolate kernels.  Every output lies between the minimum and maximum of its map; at a seed point
+    itself it is that seed's value."""
+    from . import pointnet2_utils
+    xyz = scene.point_cloud[..., :3].contiguous().float()                    # (1, N, 3)
+    known = scene.end_points["fp2_xyz"].contiguous().float()                  # (1, S, 3)
+    S = known.shape[1]
+    assert seed_map.shape[-1] == S, f"seed_map must end in the {S} seed points"
+    with torch.no_grad():
+        dist, idx = pointnet2_utils.three_nn(xyz, known)
+        recip = 1.0 / (dist + 1e-8)
+        weight = recip / recip.sum(dim=2, keepdim=True)
+        feats = seed_map.detach().float().reshape(1, -1, S).contiguous()
+        out = pointnet2_utils.three_interpolate(feats, idx, weight)           # (1, C, N)
+    return out.reshape(*seed_map.shape[:-1], xyz.shape[1])

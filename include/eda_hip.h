@@ -283,6 +283,23 @@ int eda_mha_qproj_fwd(const float *x, long x_sb, long x_sl, const float *wq, lon
                       float p_drop, const unsigned long long *seed_ptr, unsigned salt, float *q_out, long q_sb, long q_sl,
                       float *out, float *lse, int dtype, void *stream);
 
+/* The attention probabilities of a forward that has run (csrc/mha_weights.hip): what torch.nn.MultiheadAttention returns
+ * as its second value with need_weights=True -- the mean over the heads (average_attn_weights=True, per_head = 0:
+ * weights (B,Lq,Lk) dense) or every head's map (average_attn_weights=False, per_head = 1: weights (B,H,Lq,Lk) dense).
+ * The reference discards them ([0] of every call, models/encoder_decoder_layers.py:87-117, 149-153, 179-183, 366-401).
+ * q, k, strides, key_padding_mask, scale and the row alignment contract as in eda_mha_fwd; lse (B,H,Lq) is THAT forward's
+ * output for the same q, k and mask, so p = exp(scale q_h.k_h - lse[b,h,q]) needs no reduction: one launch, no workspace,
+ * no atomics, heads summed in the order 0..H-1 in registers -- two calls give the same bits.  Masked keys are exactly 0; a
+ * row whose keys are all masked (lse = -inf) is NaN, as the forward's.  p_drop > 0: every probability is multiplied by the
+ * forward's keep mask (the hash of (*seed_ptr, salt, b, h, q, k) of csrc/mha2.hip, so *seed_ptr must still hold the
+ * forward's counter) and 1/(1 - p_drop): the weights that produced `out`.  p_drop = 0 does not read seed_ptr.
+ * fp32 arithmetic whatever dtype the forward ran in.  head_dim 36, 1 <= H <= 8, any Lq, Lk >= 1; else EDA_ERR_UNSUPPORTED. */
+int eda_mha_weights_f32(const float *q, const float *k, long q_sb, long q_sl, long k_sb, long k_sl,
+                        const unsigned char *key_padding_mask, const float *lse,
+                        int B, int H, int Lq, int Lk, int head_dim, float scale,
+                        float p_drop, const unsigned long long *seed_ptr, unsigned salt,
+                        int per_head, float *weights, void *stream);
+
 /* ---- set-abstraction grouped MLP, channels-last pipeline -----------------
  * Rows are positions (scene, centre j, neighbour k) of a (b*m*ns, C) matrix.
  *
